@@ -1,14 +1,20 @@
 """bench.py — shuffle GB/s/node (partition + exchange), TeraSort 100-byte records.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload terasort|zipf|small]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL over xGMI)
 
 A step = one full shuffle of the rank's resident input: every map batch is partitioned by the
 gfx950 kernels (P1-P3) and, for N > 1, its partition-aligned share is exchanged with every other
 GPU (RCCL grouped send/recv, overlapped with the next launch group on a second stream).  At N = 1
-the reduce side resolves its blocks zero-copy from the index tables (no bytes move), and the line
-also carries BASELINE configs C4 (Zipf keys) and C5 (16-byte records, R = 10 000) as `c4` / `c5`.
-Inputs are generated on the device before timing (counter-based) and stay in HBM.
+the reduce side resolves its blocks zero-copy from the index tables (no bytes move).
+Inputs are generated on the device before timing (counter-based) and stay in HBM;
+the same arguments give the same inputs, so --dump-outputs of two builds compare array for array.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  With --full the
+line also carries the self-check, the per-kernel rooflines, the CPU baseline, the reduce-sort,
+compress, files, plugin and varlen legs, and BASELINE configs C4 (Zipf keys) and C5 (16-byte
+records, R = 10 000) as `c4` / `c5`.
 
 value = input bytes of all ranks / max-over-ranks wall time of K steps, in GB/s (1e9 B/s).
 Rank 0 prints ONE JSON line; everything else goes to stderr.
@@ -1144,6 +1150,45 @@ def launch_ranks(args) -> int:
     return 0
 
 
+def headline_only(args) -> None:
+    """A run without --full: every leg, check and probe beside the timed steps is switched off,
+    whatever its own option says."""
+    args.self_check = 0
+    args.no_cpu_baseline = True
+    args.xgmi_probe_mib = 0
+    args.c4_steps = args.c5_steps = 0
+    args.reduce_sort_records = args.varlen_rows = args.compress_maps = args.file_maps = 0
+    args.plugin_groups = args.plugin_host_maps = args.maps_2e27 = 0
+
+
+DUMP_SEED = 0x5EED0D0D
+# bytes on disk per dumped array: 40 + 8 + 8 MB, under 64 MB in all
+DUMP_BUDGET = {"map_outputs": 40_000_000, "index": 8_000_000, "index_be": 8_000_000,
+               "received": 40_000_000, "gathered_index": 8_000_000, "received_bytes": 8_000_000}
+
+
+def dump_array(path: str, t: torch.Tensor, row: int, budget: int) -> None:
+    """Write the 1-D tensor `t`, read as rows of `row` elements, to `path` (.npy): bytes as
+    float32, integers as float64 (exact below 2^53).  An array over `budget` bytes on disk is
+    cut to a fixed sample of whole rows: row numbers drawn with DUMP_SEED (numpy default_rng,
+    with replacement, sorted), the same for every run with the same shape."""
+    dt = np.float32 if t.dtype == torch.uint8 else np.float64
+    rows = t.numel() // row
+    t = t[:rows * row].view(rows, row)
+    keep = budget // (row * np.dtype(dt).itemsize)
+    if rows > keep:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).integers(0, rows, size=keep))
+        t = t[torch.from_numpy(pick).to(t.device)]
+    np.save(path, t.cpu().numpy().astype(dt).reshape(-1))
+
+
+def dump_outputs(d: str, arrays: dict, suffix: str = "") -> None:
+    """--dump-outputs: {name: (tensor, elements per row)} -> d/<name><suffix>.npy."""
+    os.makedirs(d, exist_ok=True)
+    for name, (t, row) in arrays.items():
+        dump_array(os.path.join(d, f"{name}{suffix}.npy"), t, row, DUMP_BUDGET[name])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1247,11 +1292,29 @@ def main():
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify", action="store_true",
-                    help="test mode (N>1): check every received block of every group against "
-                         "the CPU oracle; timing is then not a benchmark")
+                    help="test mode (N>1, with --full): check every received block of every "
+                         "group against the CPU oracle; timing is then not a benchmark")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures or "
+                         "checks: the untimed self-check, the per-kernel timings and rooflines, "
+                         "the CPU baseline, the exchange probe, and at N=1 the reduce-sort, 2^27-"
+                         "record maps, compress, files, plugin, varlen, C4 and C5 legs (each "
+                         "sized by its own option above).  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to "
+                         "DIR/<name>.npy (float32 / float64; a fixed seeded sample of rows where "
+                         "an array is over its share of 56 MB): N=1 map_outputs, index, index_be; "
+                         "N>1 per rank received, gathered_index, received_bytes")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:
+        if args.verify or args.force_mismatch:
+            ap.error("--verify and --force-mismatch check the run's bytes: they need --full")
+        headline_only(args)
     if args.gpus > 1 and not launched_rank():
         # no launcher: this process becomes the parent of the N ranks (before any GPU call)
         sys.exit(launch_ranks(args))
@@ -1354,7 +1417,8 @@ def main():
                 for _ in range(2)]
         ws = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(NB)]
         # one all-gathered index table per group (kept for the exact byte accounting)
-        gidx = torch.empty(groups, world * gm * (R + 1), dtype=torch.int64, device=dev)
+        # (zeroed: a short last group leaves its row's tail unwritten, and --dump-outputs reads it)
+        gidx = torch.zeros(groups, world * gm * (R + 1), dtype=torch.int64, device=dev)
         rbytes = torch.zeros(groups, dtype=torch.int64, device=dev)
         peer = [torch.empty(world, dtype=torch.int64, device=dev) for _ in range(NB)]
         part_done = [torch.cuda.Event() for _ in range(NB)]
@@ -1640,8 +1704,9 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    node.kernel_times()  # drop warm-up timings
-    node.set_kernel_timing(True)
+    if args.full:  # per-kernel durations (HIP events around every launch) for the rooflines
+        node.kernel_times()  # drop warm-up timings
+        node.set_kernel_timing(True)
     if pipelined:
         xfer_ev.clear()
     barrier()
@@ -1650,9 +1715,20 @@ def main():
         step()
     barrier()
     t1 = time.perf_counter()
-    node.set_kernel_timing(False)
-    kt = node.kernel_times()
+    if args.full:
+        node.set_kernel_timing(False)
+        kt = node.kernel_times()
     node.check()  # no kernel recorded a failure in the device error word
+    if args.dump_outputs:
+        if not pipelined:
+            dump_outputs(args.dump_outputs, {"map_outputs": (out, rs), "index": (index, 1),
+                                             "index_be": (index_be, 8)})
+        else:  # the receive ring keeps the step's last launch group
+            j = groups - 1
+            dump_outputs(args.dump_outputs,
+                         {"received": (recv[j % 2][:max(0, int(rbytes[j].item()))], rs),
+                          "gathered_index": (gidx.view(-1), 1), "received_bytes": (rbytes, 1)},
+                         suffix=f"_rank{rank}" if world > 1 else "")
 
     elapsed = t1 - t0
     if world > 1:
@@ -1663,10 +1739,6 @@ def main():
     total_bytes = n * rs * world * args.steps
     value = total_bytes / elapsed / 1e9
 
-    # ---- roofline of the dominant kernel (scatter) + the whole map-side pass --------------
-    overlapped = not pipelined and (args.map_pipeline or args.streams > 1)
-    roof, roof_map = rooflines(node, kt, elapsed, args.steps, n, rs, R, maps, args.workload,
-                               pipelined, overlapped)
     result = {
         "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -1687,11 +1759,16 @@ def main():
                                   "send/recv)" if args.transport == "rccl" else
                                   ", partition-aligned one-sided IPC pull exchange"),
                    "global_batch": n * world, "seq_len": rs, "parallelism": f"shuffle{world}"},
-        "roofline": roof,
-        "roofline_map_side": roof_map,
-        "cpu_baseline": None,
     }
-    if pipelined:
+    if pipelined and int(rbytes.min().item()) < 0:
+        raise RuntimeError("exchange overflowed a receive buffer")
+    if args.full:
+        # ---- roofline of the dominant kernel (scatter) + the whole map-side pass ----------
+        overlapped = not pipelined and (args.map_pipeline or args.streams > 1)
+        roof, roof_map = rooflines(node, kt, elapsed, args.steps, n, rs, R, maps, args.workload,
+                                   pipelined, overlapped)
+        result.update({"roofline": roof, "roofline_map_side": roof_map, "cpu_baseline": None})
+    if pipelined and args.full:
         torch.cuda.synchronize(dev)
         xms = sum(a.elapsed_time(b) for a, b in xfer_ev)
         xfer_n = len(xfer_ev)
@@ -1712,8 +1789,6 @@ def main():
             dist.all_reduce(ing[1:2])
         ing = ing.cpu().tolist()
         ingress_ratio = ing[0] / (ing[1] / world) if ing[1] else None
-        if int(rbytes.min().item()) < 0:
-            raise RuntimeError("exchange overflowed a receive buffer")
         remote *= args.steps
         peak = (world - 1) * XGMI_LINK_GBS
         ach = remote / (xms / 1e3) / 1e9 if xms and remote else None

@@ -138,3 +138,44 @@ def test_first_mismatch_is_chunked_and_exact():
     i, k = bench.first_mismatch(a, b, chunk=1024)
     assert i == 5000 and k == 1
     assert bench.first_mismatch(a, b, chunk=1 << 20) == (5000, 2)
+
+
+def test_dump_array_keeps_a_small_array_whole_and_samples_a_large_one(tmp_path):
+    """--dump-outputs: an array within its budget is written whole (bytes as float32, integers
+    as float64, exactly); a larger one is cut to whole rows drawn with a fixed seed, in rising
+    row order, the same rows on every call."""
+    rows, row = 1000, 100
+    t = torch.from_numpy(np.random.default_rng(1).integers(0, 256, rows * row, dtype=np.uint8))
+    p = str(tmp_path / "a.npy")
+    bench.dump_array(p, t, row, rows * row * 4)
+    a = np.load(p)
+    assert a.dtype == np.float32 and np.array_equal(a, t.numpy())
+    bench.dump_array(p, t, row, 50 * row * 4 + 7)
+    s = np.load(p)
+    assert s.dtype == np.float32 and s.size == 50 * row
+    where = {t[r * row:(r + 1) * row].numpy().tobytes(): r for r in range(rows)}
+    picked = [where[x.astype(np.uint8).tobytes()] for x in s.reshape(50, row)]
+    assert picked == sorted(picked) and len(set(picked)) > 40
+    bench.dump_array(p, t, row, 50 * row * 4 + 7)
+    assert np.array_equal(np.load(p), s)
+    big = torch.arange(77, dtype=torch.int64) + (1 << 40)
+    bench.dump_array(p, big, 1, 77 * 8)
+    b = np.load(p)
+    assert b.dtype == np.float64 and np.array_equal(b.astype(np.int64), big.numpy())
+
+
+def test_a_plain_run_switches_every_other_leg_off():
+    """Without --full nothing runs beside the timed steps, whatever the legs' own options say."""
+    r = subprocess.run(_bench_cmd("--help"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    import argparse
+    args = argparse.Namespace(self_check=1, no_cpu_baseline=False, xgmi_probe_mib=256, c4_steps=3,
+                              c5_steps=3, reduce_sort_records=-1, varlen_rows=-1, compress_maps=-1,
+                              file_maps=-1, plugin_groups=-1, plugin_host_maps=-1, maps_2e27=1)
+    bench.headline_only(args)
+    assert args.no_cpu_baseline is True
+    assert not any(v for k, v in vars(args).items() if k != "no_cpu_baseline")
+    r = subprocess.run(_bench_cmd("--steps", "0"), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    r = subprocess.run(_bench_cmd("--verify"), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "need --full" in r.stderr

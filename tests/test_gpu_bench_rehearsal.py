@@ -22,7 +22,8 @@ def _free_port():
 def _run(world, *args, timeout=300):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={world}", "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-one-gpu", *args]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-one-gpu", "--full",
+           *args]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout,
                        env=dict(os.environ, OMP_NUM_THREADS="1"))
     if r.returncode != 0:  # the ranks' own exceptions first (the launcher's summary is long)
@@ -82,8 +83,9 @@ def test_bench_starts_its_own_ranks():
     processes of torch.distributed.run), relays rank 0's line, and that line carries the N > 1
     self-check, the exchange roofline and the CPU baseline beside it."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu",
-           "--records", "3000000", "--map-records", "262144", "--group-maps", "2", "--steps", "1",
-           "--warmup", "0", "--plugin-groups", "0", "--cpu-records", "1000000", "--cpu-reps", "1"]
+           "--full", "--records", "3000000", "--map-records", "262144", "--group-maps", "2",
+           "--steps", "1", "--warmup", "0", "--plugin-groups", "0", "--cpu-records", "1000000",
+           "--cpu-reps", "1"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
@@ -102,8 +104,8 @@ def test_bench_starts_its_own_ranks():
 
 
 def _rccl_at_one(*args, timeout=300):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rccl-at-one", "--no-cpu-baseline",
-           *args]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rccl-at-one", "--full",
+           "--no-cpu-baseline", *args]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
 
@@ -137,3 +139,43 @@ def test_forced_mismatch_on_a_3_gb_group_reports_its_first_byte():
     # the corrupted byte: the first key byte of the group's middle record
     want = (32 << 20) // 2 * 100
     assert f"first differing byte at {want} " in r.stderr, r.stderr[-3000:]
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A run without --full: the line holds the headline (value = input bytes / ms_per_step over
+    exactly --steps steps) and none of the other legs; --dump-outputs holds the map outputs and
+    both index tables of the last step, bit-exact against the CPU oracle (6 maps, the last one
+    short, in 3 launch groups)."""
+    import numpy as np
+
+    import bench
+    from oracle import oracle as O
+
+    n, rpm = 90_001, 16_384  # 9 MB of map outputs: within the dump's budget, written whole
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+           "--warmup", "1", "--records", str(n), "--map-records", str(rpm), "--group-maps", "2",
+           "--dump-outputs", str(d)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == 1 and res["steps"] == 2 and res["warmup"] == 1
+    assert res["unit"] == "GB/s" and res["dtype"] == "u8" and res["higher_is_better"] is True
+    assert res["ms_per_step"] > 0
+    assert res["value"] == pytest.approx(n * 100 / (res["ms_per_step"] / 1e3) / 1e9, rel=2e-2)
+    for leg in ("self_check", "roofline", "roofline_map_side", "cpu_baseline", "reduce_sort",
+                "maps_2e27", "compress", "files", "plugin", "plugin_host", "varlen", "c4", "c5"):
+        assert leg not in res, leg
+    data, index, index_be = O.write_maps(O.terasort_partitioner(200),
+                                         O.gen_terasort(bench.SEEDS["terasort"], 0, n), 100, rpm)
+    assert sorted(os.listdir(d)) == ["index.npy", "index_be.npy", "map_outputs.npy"]
+    got = np.load(d / "map_outputs.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, data.astype(np.float32))
+    got = np.load(d / "index.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, index.astype(np.float64))
+    got = np.load(d / "index_be.npy")
+    assert got.dtype == np.float32
+    assert np.array_equal(got, np.frombuffer(index_be, np.uint8).astype(np.float32))

@@ -31,7 +31,7 @@ def _run(world, tmp_path, *args, timeout=400):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={world}", "--master-addr=127.0.0.1", f"--master-port={_free_port()}",
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--loopback-rccl",
-           "--no-cpu-baseline", *args]
+           "--full", "--no-cpu-baseline", *args]
     env = dict(os.environ, OMP_NUM_THREADS="1", SUX_LOOPBACK_DIR=str(tmp_path),
                SUX_LOOPBACK_LOG="1", SUX_LOOPBACK_TIMEOUT="150")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)

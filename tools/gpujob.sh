@@ -8,7 +8,7 @@
 #   tests [pytest args]     the -m gpu suite (or the given paths), stops at the first failure
 #   smoke                   __graft_entry__.smoke()
 #   bench [bench args]      bench.py (default: the driver's N = 1 line) -> bench.json
-#   final                   tests + smoke + default bench (a round checkpoint)
+#   final                   tests + smoke + the --full bench (a round checkpoint)
 #   trace [bench args]      rocprofv3 --kernel-trace --stats of a headline-only bench run
 #   pmc WORKLOAD...         profiles/collect_pmc.py passes (one counter group per rocprofv3 run)
 #   sortpmc                 PMC passes of tools/sort_prof.py (5 M TeraSort records)
@@ -46,7 +46,7 @@ case $job in
   tests) run_tests "$@" ;;
   smoke) run_smoke ;;
   bench) run_bench "$@" ;;
-  final) run_tests && run_smoke && run_bench ;;
+  final) run_tests && run_smoke && run_bench --full ;;
   trace)
     timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
       python3 bench.py --steps 5 --warmup 2 $LEGS --self-check 0 "$@" > $O/prof.json 2> $O/prof.err
